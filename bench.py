@@ -21,6 +21,10 @@ the contract's synchronize() and, with N > 1, as the control plane only (gloo: h
 barrier, max over ranks).  A rank that dies or hangs ends the job: the exchange's waits are bounded (SIFTMI_EXCHANGE_TIMEOUT_S),
 the error propagates as an exception, the process exits non-zero; nothing is restarted or re-executed.
 
+`--dump-outputs DIR`: after the timed steps, rank 0's packed results of the last timed step (what FrameStream.results_host returns)
+go to DIR/<name>.npy in float64 / float32, at most 64 MB (descriptors beyond that: a fixed seeded sample, the rows kept beside them).
+The frames are seeded, so two builds run with the same arguments can be compared array for array.
+
 `--gpus N` with N > 1 and no torchrun environment: this process spawns the N ranks itself (before any
 GPU call) and relays rank 0's line; it exits non-zero if fewer than N devices are visible or the
 process group does not come up with N ranks.
@@ -266,6 +270,42 @@ def self_launch(args):
     return 0
 
 
+DUMP_BUDGET = 64 * 1024 * 1024            # --dump-outputs: bytes written in all, at most
+
+
+def _sample_rows(n, cap, seed):
+    """Row indices 0 ... n-1 when n <= cap, else a sorted sample of cap of them drawn with a fixed seed (same n -> same rows)."""
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(seed).choice(n, size=cap, replace=False))
+
+
+def dump_outputs(res, out_dir):
+    """--dump-outputs: the packed results of one step as a caller of FrameStream.results_host receives them, as .npy files in float64
+    (every field of a record, in dtype order: exact for int32 and float32) and float32 (descriptor features: exact for uint8).
+    Records beyond the budget are sampled (_sample_rows); *_rows.npy say which rows were kept."""
+    kp, ds = res["keypoints"], res["descriptors"]
+    kp_cols = [kp[f].astype(np.float64) for f in kp.dtype.names]
+    kp_rows = _sample_rows(len(kp), (DUMP_BUDGET // 4) // (8 * len(kp_cols) + 8), 1)
+    ds_rows = _sample_rows(len(ds), (DUMP_BUDGET // 2) // (4 * 128 + 8 * 2 + 8), 2)
+    arrays = {
+        "counts": res["counts"].astype(np.float64),                                     # [keypoints / descriptors][frame][octave]
+        "totals": np.array([res["n_keypoints"], res["n_descriptors"]], np.float64),
+        "keypoints": np.stack(kp_cols, axis=1)[kp_rows],                                 # columns: keypoint_dtype fields
+        "keypoint_rows": kp_rows.astype(np.float64),
+        "descriptors": ds["features"][ds_rows].astype(np.float32),                      # [rows, 128]
+        "descriptor_keypoint_theta": np.stack([ds["keypoint"][ds_rows].astype(np.float64), ds["theta"][ds_rows].astype(np.float64)], axis=1),
+        "descriptor_rows": ds_rows.astype(np.float64),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET - 4096, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("dump-outputs: %s (%.1f MB; %d of %d keypoints, %d of %d descriptors)" %
+        (out_dir, total / 1e6, len(kp_rows), len(kp), len(ds_rows), len(ds)))
+
+
 def timed_steps(step, barrier, steps, warmup):
     for _ in range(warmup):
         step()
@@ -297,6 +337,9 @@ def main():
     ap.add_argument("--no-cpu", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="skip single_frame / host_io / dense")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write rank 0's results of the last timed step to DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB: records beyond that are a fixed seeded sample); the inputs are the same on every run")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -480,6 +523,8 @@ def main():
         raise SystemExit("bench: results of the last timed step differ from the first step (%d/%d vs %d/%d keypoints/descriptors): "
                          "the timed region did not compute the workload" %
                          (res["n_keypoints"], res["n_descriptors"], first["n_keypoints"], first["n_descriptors"]))
+    if args.dump_outputs and rank == 0:
+        dump_outputs(res, args.dump_outputs)
     d2h_bytes = int(res["keypoints"].nbytes + res["descriptors"].nbytes + res["counts"].nbytes)
     log("rank0 per-step: %d keypoints, %d descriptors over %d frames; %.3f ms/step, %.3f ms/frame (host-fed, results to host)" %
         (res["n_keypoints"], res["n_descriptors"], F, ms_per_step, ms_per_step / F))

@@ -99,7 +99,8 @@ typedef struct siftmi_config {
     int32_t graph_fork;                 /* the captured launch sequence of siftmi_detect_describe_batch_device forks into one chain per
                                            octave (octave k's scan and keypoint stages beside octave k+1's pyramid): 0 = default (on,
                                            unless a frame's first octave exceeds 48 Mpixel), 1 = always, -1 = never (every kernel
-                                           alone on the GPU: what a per-kernel profile wants) */
+                                           alone on the GPU: what a per-kernel profile wants).  On a HIP runtime older than 7.2
+                                           the sequence is always one chain (siftmi_graph_stats reports which ran) */
     int32_t descriptor_patch_lds;       /* 1 = the descriptor kernel of large launches stages every 16 x 16-sample tile of a window (18 x 18
                                            texels) in LDS and samples from there instead of reading the layer through the caches; the
                                            descriptors are byte-identical, the stage is slower (profiles/desc_patch_lds_r05.log): 0 = default */

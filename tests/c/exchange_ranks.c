@@ -17,6 +17,8 @@
  *                   int32 world, complete_at_first_look, complete_when_read, 0; int64 kp_records, desc_records
  *                   per rank r: int32 totals[4]; counts (n_counts); min(totals[0], kp_records) x 44 B; min(totals[1], desc_records) x 136 B
  *                 trailer: int64 -1; int64 regathered_steps, overflow_steps, gathers, bytes_last
+ *   EXCHANGE_RANKS_DEVICE (environment, default 0): the HIP device of this rank (the parent test spreads real-RCCL ranks over the
+ *               devices when there are enough of them; otherwise every rank shares device 0)
  * Exit codes: 0 ok, 3 the exchange timed out / was aborted (a peer is gone), 77 the transport refused this layout (real RCCL with
  * two ranks on one GPU), anything else a failure. */
 #include <signal.h>
@@ -93,14 +95,16 @@ int main(int argc, char **argv) {
     else if (sscanf(scenario, "overflow:%d", &overflow_rank) == 1) {}
     else if (strcmp(scenario, "plain") != 0) { fprintf(stderr, "unknown scenario %s\n", scenario); return 1; }
 
-    if (siftmi_device_count() < 1) { fprintf(stderr, "no HIP device\n"); return 78; }
+    const char *dev_env = getenv("EXCHANGE_RANKS_DEVICE");
+    const int device = dev_env ? atoi(dev_env) : 0;
+    if (siftmi_device_count() <= device || device < 0) { fprintf(stderr, "no HIP device %d\n", device); return 78; }
     siftmi_config cfg;
     CHECK(siftmi_default_config(&cfg, W, H));
     cfg.n_octaves = n_oct;
     cfg.max_batch = F;
     if (rank == overflow_rank) cfg.max_keypoints = 8;
     siftmi_ctx *ctx = NULL;
-    CHECK(siftmi_create(&cfg, 0, &ctx));                                   /* every rank on device 0: the ranks share the one GPU of the box */
+    CHECK(siftmi_create(&cfg, device, &ctx));
 
     siftmi_stream_config scfg;
     CHECK(siftmi_stream_default_config(&scfg, F));
@@ -146,7 +150,7 @@ int main(int argc, char **argv) {
     void *h_tmp = malloc(set_bytes);
     for (int j = 0; j < 2; j++) {
         if (fread(h_tmp, 1, set_bytes, fin) != set_bytes) { fprintf(stderr, "short read of %s\n", argv[12]); return 1; }
-        CHECK(siftmi_device_alloc(0, set_bytes, &d_sets[j]));
+        CHECK(siftmi_device_alloc(device, set_bytes, &d_sets[j]));
         CHECK(siftmi_memcpy(d_sets[j], h_tmp, set_bytes, 0));
     }
     free(h_tmp);

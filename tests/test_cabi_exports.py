@@ -162,6 +162,44 @@ def test_bench_refuses_more_gpus_than_visible():
     assert p.returncode != 0 and b"WORLD_SIZE is 2" in p.stderr
 
 
+def test_bench_dump_outputs_files(tmp_path):
+    """bench.py --dump-outputs writes a step's packed results as float32 / float64 .npy files within 64 MB: every record field exactly,
+    records beyond the budget as the same seeded sample on every run (here: a step larger than the budget, built on the host)."""
+    import sys
+    from siftmetal_amd import _capi
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(5)
+    nk, nd, F, O = 150000, 150000, 4, 3
+    kp = np.zeros(nk, _capi.keypoint_dtype)
+    for f in kp.dtype.names:
+        kp[f] = rng.integers(-2 ** 31, 2 ** 31 - 1, nk) if kp.dtype[f].kind == "i" else rng.normal(0, 1e3, nk)
+    ds = np.zeros(nd, _capi.descriptor_dtype)
+    ds["keypoint"] = np.arange(nd) // 2
+    ds["theta"] = rng.uniform(-np.pi, np.pi, nd)
+    ds["features"] = rng.integers(0, 256, (nd, 128))
+    counts = rng.integers(0, 2 ** 20, (2, F, O)).astype(np.int32)
+    res = {"keypoints": kp, "descriptors": ds, "counts": counts, "n_keypoints": nk, "n_descriptors": nd}
+    bench.dump_outputs(res, str(tmp_path / "a"))
+    bench.dump_outputs(res, str(tmp_path / "b"))
+    names = sorted(os.listdir(str(tmp_path / "a")))
+    assert names == sorted(["counts.npy", "totals.npy", "keypoints.npy", "keypoint_rows.npy", "descriptors.npy", "descriptor_keypoint_theta.npy",
+                            "descriptor_rows.npy"])
+    assert sum(os.path.getsize(str(tmp_path / "a" / n)) for n in names) <= 64 * 1024 * 1024
+    got = {n[:-4]: np.load(str(tmp_path / "a" / n)) for n in names}
+    for n, a in got.items():
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / (n + ".npy")))), n
+    assert np.array_equal(got["counts"], counts) and list(got["totals"]) == [nk, nd]
+    kr, dr = got["keypoint_rows"].astype(np.int64), got["descriptor_rows"].astype(np.int64)
+    assert len(kr) == nk and 0 < len(dr) < nd and np.all(np.diff(dr) > 0) and dr[-1] < nd     # all keypoints fit; descriptors sampled, sorted, distinct
+    for j, f in enumerate(kp.dtype.names):
+        assert np.array_equal(got["keypoints"][:, j], kp[f][kr].astype(np.float64)), f
+    assert np.array_equal(got["descriptors"], ds["features"][dr].astype(np.float32))
+    assert np.array_equal(got["descriptor_keypoint_theta"][:, 0], ds["keypoint"][dr]) and \
+        np.array_equal(got["descriptor_keypoint_theta"][:, 1], ds["theta"][dr].astype(np.float64))
+
+
 def test_asm_prefetch_registers_are_not_touched_in_flight():
     """extrema_kernel issues its row loads as asm statements the compiler does not count (three rows ahead) and waits with a
     hand-counted vmcnt; hipcc may legally copy or reuse such a destination VGPR before the data lands.  The generated ISA is

@@ -2,7 +2,8 @@
 
 One process per rank (tests/c/exchange_ranks.c, plain C against include/siftmi.h), all on device 0, the collectives carried by
 the test transport tests/c/libfake_rccl.so (librccl's entry points over shared memory; SIFTMI_RCCL_LIB) because real RCCL
-refuses two ranks on one GPU -- the same test is also parametrised on the real librccl and skips when it refuses.  What is
+refuses two ranks on one GPU -- the same test is also parametrised on the real librccl, which runs rank r on device r where
+there are enough devices and otherwise must refuse the shared device cleanly on every rank (run_ranks).  What is
 under test is the C exchange itself, unchanged: the totals all-gather, step-late payload sizing, the re-gather of a step that
 outgrew its sizes, the rotation of the two gathered sets against the stream's result sets, event ordering between the launch
 streams and the gather stream, overflow propagation.  (BASELINE configs[3] is this path on 8 GPUs.)"""
@@ -76,9 +77,14 @@ def parse_rank_output(path, world, steps):
 
 
 def run_ranks(tmp_path, world, scenario, pipeline, synchronous, transport, steps=8, tag=""):
-    """Spawns `world` fresh processes on device 0; returns (per-rank parsed output, per-rank summary) or skips."""
+    """Spawns `world` fresh processes; returns (per-rank parsed output, per-rank summary), or None when real RCCL refused the layout.
+    The test transport runs every rank on device 0.  Real RCCL gets rank r on device r when there are `world` devices; otherwise
+    the ranks share device 0, which RCCL refuses (duplicate GPU) -- then every rank must fail at once and cleanly: exit code 77
+    with the ncclCommInitRank error, none hanging, none crashing."""
     import __graft_entry__ as ge
+    from siftmetal_amd import _capi
     ge.build()
+    spread = transport == "rccl" and _capi.load().siftmi_device_count() >= world
     d = tmp_path / ("run_%s_%d_%s_p%d_s%d%s" % (transport, world, scenario.replace(":", "_"), pipeline, synchronous, tag))
     d.mkdir()
     env = dict(os.environ)
@@ -94,7 +100,7 @@ def run_ranks(tmp_path, world, scenario, pipeline, synchronous, transport, steps
         np.concatenate([small, large]).tofile(str(d / ("frames%d.bin" % r)))
         cmd = [EXE, str(W), str(H), str(N_OCT), str(F), str(r), str(world), str(steps), scenario, str(pipeline), str(synchronous),
                str(d / "unique_id"), str(d / ("frames%d.bin" % r)), str(d / ("out%d.bin" % r))]
-        procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env))
+        procs.append(subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=dict(env, EXCHANGE_RANKS_DEVICE=str(r if spread else 0))))
     outs, timed_out = [], False
     for p in procs:
         try:
@@ -106,10 +112,11 @@ def run_ranks(tmp_path, world, scenario, pipeline, synchronous, transport, steps
                     q.kill()
             o, e = p.communicate()
         outs.append((p.returncode, o.decode("utf-8", "replace"), e.decode("utf-8", "replace")))
-    if transport == "rccl" and (timed_out or any(rc == 77 for rc, _, _ in outs)):
-        pytest.skip("real RCCL does not run %d ranks on one device here (%s): %s" %
-                    (world, "timed out" if timed_out else "ncclCommInitRank refused", outs[0][2][-300:].strip()))
     assert not timed_out, [(rc, e[-1500:]) for rc, _, e in outs]
+    if transport == "rccl" and not spread and any(rc == 77 for rc, _, _ in outs):
+        for r, (rc, _, e) in enumerate(outs):
+            assert rc == 77 and "rank %d: siftmi_exchange_create" % r in e and "ncclCommInitRank" in e, (r, rc, e[-1500:])
+        return None
     for r, (rc, o, e) in enumerate(outs):
         assert rc == 0, (r, rc, e[-2000:])
         assert "rank %d ok %d steps" % (r, steps) in o
@@ -136,10 +143,14 @@ def test_exchange_ranks_jump_on_one_rank_is_regathered(tmp_path, world, pipeline
     """2, 3 and 4 ranks, two steps in flight (and one: two result sets against the exchange's two gathered sets), sizes from the previous step.  Rank world-1 alone runs its large frame set at step 3
     (> 1.5x the records): every rank's first look at step 3 is cut short (complete = 0) -- all ranks see the same totals and
     take the same decision --, the next gather call repeats that step in full from its intact result set, and every rank's view
-    of every step, read one step late, holds every rank's own packed results byte for byte.  regathered_steps == 1."""
+    of every step, read one step late, holds every rank's own packed results byte for byte.  regathered_steps == 1.  Real RCCL
+    with fewer devices than ranks: every rank's refusal of the shared device, checked in run_ranks."""
     import siftmetal_amd as sm
     steps, K, R = 8, 3, world - 1
-    per_rank, summary = run_ranks(tmp_path, world, "jump:%d:%d" % (K, R), pipeline, 0, transport, steps)
+    got = run_ranks(tmp_path, world, "jump:%d:%d" % (K, R), pipeline, 0, transport, steps)
+    if got is None:
+        return                                                   # real RCCL, ranks sharing one device: the refusal is what run_ranks checked
+    per_rank, summary = got
     check_every_view_equals_every_ranks_own_results(per_rank, world, steps)
     # the C hosts' own results are the host API's results for the same frames
     eng = sm.Engine(W, H, n_octaves=N_OCT, max_batch=F)
@@ -225,8 +236,11 @@ def test_exchange_rank_dies_and_the_others_abort_within_the_deadline(tmp_path, p
     try:
         for r in range(world):
             if r != R:
-                procs[r].wait(timeout=30)
-                ends[r] = time.monotonic() - t_dead
+                try:
+                    procs[r].wait(timeout=30)
+                    ends[r] = time.monotonic() - t_dead
+                except subprocess.TimeoutExpired:
+                    ends[r] = None                                # still running 30 s after the kill: fails below, with its stderr
     finally:
         for q in procs:                                           # exactly the processes started here
             if q.poll() is None:
@@ -237,8 +251,8 @@ def test_exchange_rank_dies_and_the_others_abort_within_the_deadline(tmp_path, p
         if r == R:
             assert "dying at step %d" % K in e
             continue
+        assert ends[r] is not None and ends[r] < 10.0, (r, ends, e[-1500:])
         assert procs[r].returncode == 3, (r, procs[r].returncode, e[-1500:])
-        assert ends[r] < 10.0, ends
         assert "rank %d of %d" % (r, world) in e and "timed out" in e and ("step %d" % K) in e and "communicator aborted" in e, e[-1500:]
         assert "rank %d ok" % r not in o.decode()
 
